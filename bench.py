@@ -23,7 +23,25 @@ metric: "Gkeys/s and achieved HBM GB/s (% of peak), u32 keys N=2^30, 1/2/4/8 GPU
   with exactly its share of the global order, whatever the distribution.
 
 Timing: W warm-up steps, then barrier + synchronize, K steps, synchronize +
-barrier; the max over ranks.  rank 0 prints ONE JSON line.  `roofline` prices
+barrier; the max over ranks.  rank 0 prints ONE JSON line.  When K fresh
+inputs do not fit in HBM the K steps run in groups of as many as fit, the
+inputs regenerated between the groups outside the timing.
+
+A plain run does only that: set-up, warm-up, the K timed steps, the device
+error word and the sortedness of the last step's output, --dump-outputs, the
+line.  Everything else is behind --full: the multiset / stability checks, the
+per-launch roofline pass, `cpu_baseline`, `vendor`, `reference_gpu` and the
+multi-GPU per-phase breakdown (each still has its own off switch).
+
+--dump-outputs DIR writes what the last timed step returned to its caller --
+the sorted keys and, for sortPairs, the permuted values -- as DIR/keys.npy,
+DIR/values.npy: a fixed seeded sample of DUMP_ROWS rows (all of them when
+there are fewer) with DIR/sample_index.npy naming the rows.  Float keys are
+saved as their values; integer keys and payloads as their 32-bit words, low
+word first, in float64 (exact).  The inputs are the same draws in every run,
+so two builds can be compared array for array.
+
+With --full, `roofline` prices
 the DOMINANT kernel -- the kernel with the most time per sort -- at its own
 algorithmic bytes per launch, from per-launch HIP events on the sort's own
 stream inside the timed region (gated launches that found nothing to do,
@@ -82,6 +100,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="also run the extra checks, the roofline pass and the CPU / vendor / reference baselines")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed step's output (a fixed sample of it) as DIR/<name>.npy")
+    p.add_argument("--max-inputs", type=int, default=None,
+                   help="N=1: hold at most this many fresh input buffers (default: as many of --steps as fit in HBM)")
     p.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     p.add_argument("--n", type=int, default=None, help="keys per GPU (default: the workload's)")
     p.add_argument("--vendor", default="auto", choices=["auto", "off"],
@@ -344,6 +368,37 @@ def build_roofline(prof, kern, steps, n, kb, vb, pinfo, elapsed, global_keys, wo
     return roof
 
 
+DUMP_ROWS = 1 << 20    # at most 6 words a row (u64 key + 16-B payload) in float64: 48 MiB + the index
+
+
+def dump_outputs(out_dir, kt, kb, vb, keys, vals, n, suffix=""):
+    """--dump-outputs: the sorted keys (and values) in `keys` / `vals` (device
+    byte buffers of n rows) at a fixed, seeded sample of rows -> .npy files."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if n > DUMP_ROWS:   # both ends and a seeded draw of the rows between, ascending
+        idx = np.concatenate([[0], np.sort(np.random.default_rng(0).integers(1, n - 1, DUMP_ROWS - 2)), [n - 1]])
+    else:
+        idx = np.arange(n)
+    idx = idx.astype(np.int64)
+    idx_d = torch.from_numpy(idx).cuda()
+
+    def words(buf, width):   # u32 words of the sampled rows, [rows, width / 4]
+        w = buf[:n * width].view(torch.int32).view(n, width // 4)
+        return np.ascontiguousarray(w.index_select(0, idx_d).cpu().numpy()).view(np.uint32)
+
+    def as_f64(w):
+        return w.astype(np.float64).reshape(-1) if w.shape[1] == 1 else w.astype(np.float64)
+
+    k = words(keys, kb)
+    karr = k.view(np.float32).reshape(-1) if kt == 2 else k.view(np.float64).reshape(-1) if kt == 3 else as_f64(k)
+    np.save(os.path.join(out_dir, f"keys{suffix}.npy"), karr)
+    if vb:
+        np.save(os.path.join(out_dir, f"values{suffix}.npy"), as_f64(words(vals, vb)))
+    np.save(os.path.join(out_dir, f"sample_index{suffix}.npy"), idx.astype(np.float64))
+
+
 def cpu_model() -> str:
     try:
         for line in open("/proc/cpuinfo"):
@@ -439,14 +494,14 @@ def main():
         tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device="cuda")
         # Every TIMED step sorts its own fresh buffer (the reference draws a new
         # stream per run, unittest.cpp:544-549): `steps` distinct buffers must
-        # fit in HBM, else fail loudly -- inputs are never recycled.
+        # fit in HBM, else the steps run in groups of as many as fit, refilled
+        # between the groups outside the timing -- inputs are never recycled.
         free, _total = torch.cuda.mem_get_info()
         per = n * (kb + vb)
         fit = int((free - tmp_bytes - (6 << 30)) // max(per, 1))
-        if fit < steps:
-            raise SystemExit(f"bench: {steps} fresh inputs of {per / 2**30:.1f} GiB do not fit in HBM "
-                             f"(room for {fit}); use fewer --steps")
-        pool = steps
+        if fit < 1:
+            raise SystemExit(f"bench: an input of {per / 2**30:.1f} GiB does not fit in HBM")
+        pool = max(1, min(steps, fit, args.max_inputs or steps))
 
         def gen(buf, i):        # run r consumes stream draws r*N+1 .. (r+1)*N
             if dist_kind == "uniform":
@@ -464,9 +519,8 @@ def main():
                 TU.iota(vb, vbuf, n)
                 vals.append(vbuf)
         keys_in0 = None
-        if vb:      # keep one input for the stability/gather check of the last step
+        if vb and args.full and not args.unchecked:   # one input kept for the stability/gather check of the last step
             keys_in0 = torch.empty(n * kb, dtype=torch.uint8, device="cuda")
-            keys_in0.copy_(keys[pool - 1])
         torch.cuda.synchronize()
 
         def step(j):
@@ -483,63 +537,81 @@ def main():
             gen(keys[i], i)
             if vb:
                 TU.iota(vb, vals[i], n)
-        # keys-only: an order-independent fingerprint of every timed input
-        # (checked against its output after the timed region: a dropped or
-        # duplicated key cannot pass as sorted output)
-        fps = [TU.fingerprint(kt, keys[i], n) for i in range(steps)] if not vb and not args.unchecked else None
-        torch.cuda.synchronize()
-        barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(steps):
-            step(i)
-        torch.cuda.synchronize()
-        barrier()
-        t1 = time.perf_counter()
-        big_keys = T.debug_big_keys(tmp, kt, vb, n, stream)   # the last sort's fallback work (0: none)
-        rs.checkDeviceError(tmp)      # raises on a look-back / claim timeout in any timed step
+        # --full, keys-only: an order-independent fingerprint of every timed
+        # input (checked against its output after the timed region: a dropped
+        # or duplicated key cannot pass as sorted output)
+        check_fp = args.full and not vb and not args.unchecked
+        elapsed, lost, done, m = 0.0, [], 0, 0
+        while done < steps:     # one group when all K inputs fit (pool == steps)
+            m = min(pool, steps - done)
+            if done:            # refill: step r sorts draws r*N+1 .. (r+1)*N
+                for i in range(m):
+                    gen(keys[i], done + i)
+                    if vb:
+                        TU.iota(vb, vals[i], n)
+            if keys_in0 is not None and done + m == steps:
+                keys_in0.copy_(keys[m - 1])
+            fps = [TU.fingerprint(kt, keys[i], n) for i in range(m)] if check_fp else None
+            torch.cuda.synchronize()
+            barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(m):
+                step(i)
+            torch.cuda.synchronize()
+            barrier()
+            t1 = time.perf_counter()
+            elapsed += t1 - t0
+            rs.checkDeviceError(tmp)      # raises on a look-back / claim timeout in a timed step
+            if fps is not None:
+                lost += [done + i for i in range(m) if TU.fingerprint(kt, keys[i], n) != fps[i]]
+            done += m
         # correctness of the last timed step (outside the timed region)
-        last = steps - 1
+        last = m - 1
         bad = 0 if args.unchecked else TU.count_unsorted(kt, keys[last], n, 0, kb * 8)
         if bad:
             raise SystemExit(f"bench: output of the last step is not sorted ({bad} inversions)")
-        if fps is not None:
-            lost = [i for i in range(steps) if TU.fingerprint(kt, keys[i], n) != fps[i]]
-            if lost:
-                raise SystemExit(f"bench: steps {lost} lost or duplicated keys (multiset fingerprint differs)")
-        if vb and not args.unchecked:
+        if lost:
+            raise SystemExit(f"bench: steps {lost} lost or duplicated keys (multiset fingerprint differs)")
+        if keys_in0 is not None:
             chk = TU.check_pairs(kt, vb, keys_in0, keys[last], vals[last], n, 0, kb * 8)
             if chk["gather_mismatch"] or chk["unstable"]:
                 raise SystemExit(f"bench: pairs output of the last step is wrong: {chk}")
-        # per-launch kernel times for the roofline: the same K steps again, on
-        # regenerated inputs, with HIP events around every launch on the sort's
-        # stream.  Those events cost ~0.1 ms per sort (scripts/prof_overhead.py),
-        # so they are kept out of the timed region above.
-        for i in range(steps):
-            gen(keys[i], i)
-            if vb:
-                TU.iota(vb, vals[i], n)
-        torch.cuda.synchronize()
-        T.profile_enable(True)
-        t2 = time.perf_counter()
-        for i in range(steps):
-            step(i)
-        torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        prof = {k: T.profile_launches(k) for k in range(4)}
-        kern = {k: T.profile_launch_kernels(k) for k in range(4)}
-        T.profile_enable(False)
-        rs.checkDeviceError(tmp)
-        ev_ms = (t3 - t2) / steps * 1e3
-        vendor = ref_gpu = None
-        if args.vendor == "auto" and world == 1:
-            del keys_in0
-            vendor = vendor_bench(T, TU, kt, kb, vb, n, keys, vals, gen, stream)
-        # (the reference's kernels index with 32-bit ints: up to 2^30 keys here)
-        if args.ref_gpu == "auto" and world == 1 and dist_kind == "uniform" and n <= (1 << 30):
-            ref_gpu = reference_gpu_bench(TU, kt, kb, vb, n, keys, vals, gen, stream)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, kt, kb, vb, keys[last], vals[last] if vb else None, n)
+        prof = kern = ev_ms = vendor = ref_gpu = None
+        big_keys = psteps = 0
+        if args.full:
+            big_keys = T.debug_big_keys(tmp, kt, vb, n, stream)   # the last sort's fallback work (0: none)
+            # per-launch kernel times for the roofline: the same steps again
+            # (one group of them), on regenerated inputs, with HIP events around
+            # every launch on the sort's stream.  Those events cost ~0.1 ms per
+            # sort (scripts/prof_overhead.py), so they are kept out of the
+            # timed region above.
+            psteps = pool
+            for i in range(psteps):
+                gen(keys[i], i)
+                if vb:
+                    TU.iota(vb, vals[i], n)
+            torch.cuda.synchronize()
+            T.profile_enable(True)
+            t2 = time.perf_counter()
+            for i in range(psteps):
+                step(i)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            prof = {k: T.profile_launches(k) for k in range(4)}
+            kern = {k: T.profile_launch_kernels(k) for k in range(4)}
+            T.profile_enable(False)
+            rs.checkDeviceError(tmp)
+            ev_ms = (t3 - t2) / psteps * 1e3
+            if args.vendor == "auto" and world == 1:
+                del keys_in0
+                vendor = vendor_bench(T, TU, kt, kb, vb, n, keys, vals, gen, stream)
+            # (the reference's kernels index with 32-bit ints: up to 2^30 keys here)
+            if args.ref_gpu == "auto" and world == 1 and dist_kind == "uniform" and n <= (1 << 30):
+                ref_gpu = reference_gpu_bench(TU, kt, kb, vb, n, keys, vals, gen, stream)
         inputs = "fresh per step"
-        elapsed = t1 - t0
         parallelism = "single"
         phase = None
     else:
@@ -573,7 +645,8 @@ def main():
         for i in range(warmup):
             out = step(i)
         phase_s = {}
-        out = step(0, phase_s)                     # untimed per-phase breakdown (synchronising)
+        if args.full:
+            out = step(0, phase_s)                 # untimed per-phase breakdown (synchronising)
         del out
         torch.cuda.synchronize()
         barrier()
@@ -584,21 +657,26 @@ def main():
         torch.cuda.synchronize()
         barrier()
         t1 = time.perf_counter()
-        # per-launch kernel times (HIP events around every launch): a second
-        # pass of the same steps, outside the timed region (as single-GPU)
-        T.profile_enable(True)
-        t2 = time.perf_counter()
-        for i in range(steps):
-            out2 = step(warmup + i)
-        torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        prof = {k: T.profile_launches(k) for k in range(4)}
-        kern = {k: T.profile_launch_kernels(k) for k in range(4)}
-        big_keys = 0
-        T.profile_enable(False)
-        del out2
-        ev_ms = (t3 - t2) / steps * 1e3
-        ko, _vo, n_out = out
+        prof = kern = ev_ms = None
+        big_keys, psteps = 0, steps
+        if args.full:
+            # per-launch kernel times (HIP events around every launch): a second
+            # pass of the same steps, outside the timed region (as single-GPU)
+            T.profile_enable(True)
+            t2 = time.perf_counter()
+            for i in range(steps):
+                out2 = step(warmup + i)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            prof = {k: T.profile_launches(k) for k in range(4)}
+            kern = {k: T.profile_launch_kernels(k) for k in range(4)}
+            T.profile_enable(False)
+            del out2
+            ev_ms = (t3 - t2) / steps * 1e3
+        ko, vo, n_out = out
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, kt, kb, vb, ko, vo if vb else None, n_out,
+                         f"_rank{rank}" if world > 1 else "")
         bad = TU.count_unsorted(kt, ko, n_out, 0, kb * 8)
         if bad:
             raise SystemExit(f"bench: rank {rank} output is not sorted ({bad} inversions)")
@@ -625,8 +703,10 @@ def main():
         vendor = ref_gpu = None
         elapsed = t1 - t0
         parallelism = f"bucket-exchange x{world} (RCCL all_gather + grouped point-to-point exchange)"
-        phase = {k: round(v * 1e3, 3) for k, v in phase_s.items()}
-        phase["n_out_rank0"] = n_out if rank == 0 else None
+        phase = None
+        if args.full:
+            phase = {k: round(v * 1e3, 3) for k, v in phase_s.items()}
+            phase["n_out_rank0"] = n_out if rank == 0 else None
 
     # max over ranks
     el = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -636,20 +716,22 @@ def main():
     ms_per_step = elapsed / steps * 1e3
     value = global_keys / (elapsed / steps) / 1e9
 
-    # roofline of the DOMINANT kernel kind (device passes, local sort or the
-    # per-bucket fallback's passes: the most time inside the timed region);
-    # algorithmic bytes per launch = 2 * n * (K + V) (one read and one write of
-    # every key and value); gated launches that found nothing
-    # to do (< GATED_NOOP_MS) are not launches of the kernel's work
-    cfg_info = T.RadixSort.Config(keyType=T.KeyType(kt), valueType={0: T.ValueType.U32, 4: T.ValueType.U32,
-                                                                     8: T.ValueType.U64, 16: T.ValueType.U128}[vb])
-    pinfo = T.RadixSort([], cfg_info, T.Options(**dict(kv.split("=", 1) for kv in args.opt.split(",") if kv))).pathInfo(
-        n, 0, kb * 8, bool(vb)) if not use_dist else None
-    roof = build_roofline(prof, kern, steps, n, kb, vb, pinfo, elapsed, global_keys, world, wl, big_keys)
-
-    cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto":
-        cpu = cpu_baseline(kt, vb, args.cpu_seconds)
+    roof = cpu = None
+    if args.full:
+        # roofline of the DOMINANT kernel kind (device passes, local sort or the
+        # per-bucket fallback's passes: the most time inside the timed region);
+        # algorithmic bytes per launch = 2 * n * (K + V) (one read and one write of
+        # every key and value); gated launches that found nothing
+        # to do (< GATED_NOOP_MS) are not launches of the kernel's work
+        cfg_info = T.RadixSort.Config(keyType=T.KeyType(kt), valueType={0: T.ValueType.U32, 4: T.ValueType.U32,
+                                                                         8: T.ValueType.U64, 16: T.ValueType.U128}[vb])
+        pinfo = T.RadixSort([], cfg_info, T.Options(**dict(kv.split("=", 1) for kv in args.opt.split(",") if kv))
+                            ).pathInfo(n, 0, kb * 8, bool(vb)) if not use_dist else None
+        # (the profiled pass ran psteps of the K steps: the timed region's share of them)
+        roof = build_roofline(prof, kern, psteps, n, kb, vb, pinfo, elapsed * psteps / steps, global_keys, world, wl,
+                              big_keys)
+        if rank == 0 and world == 1 and args.cpu_baseline == "auto":
+            cpu = cpu_baseline(kt, vb, args.cpu_seconds)
 
     if rank == 0:
         out = {"metric": METRIC, "value": round(value, 3), "unit": "Gkeys/s", "n_gpus": world, "steps": steps,
@@ -664,10 +746,13 @@ def main():
                           "distribution": dist_name,
                           "inputs": inputs},
                "roofline": roof, "cpu_baseline": cpu, "vendor": vendor, "reference_gpu": ref_gpu,
-               "timing": {"ms_per_step_with_launch_events": round(ev_ms, 4),
-                          "note": "value / ms_per_step: K sorts between a barrier + synchronize on both sides, "
-                                  "no per-launch events; roofline per-launch times: a second pass of the same K "
-                                  "steps with HIP events around every launch (their cost is the difference)"}}
+               "full": args.full,
+               "timing": {"ms_per_step_with_launch_events": None if ev_ms is None else round(ev_ms, 4),
+                          "timed_groups": -(-steps // pool) if not use_dist else 1,
+                          "note": "value / ms_per_step: K sorts between a barrier + synchronize on both sides "
+                                  "(in timed_groups groups when K fresh inputs do not fit in HBM), "
+                                  "no per-launch events; --full: roofline per-launch times from a second pass of "
+                                  "the same steps with HIP events around every launch (their cost is the difference)"}}
         if phase:
             out["phases_ms"] = phase
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -40,6 +40,7 @@ for step in "$@"; do
       wl=${arg%%,*}
       extra=""
       [[ "$arg" == *,* ]] && extra=$(echo "${arg#*,}" | tr ',' ' ')
+      extra="--full $extra"   # the whole line: roofline, baselines, extra checks
       timeout -k 10 600 python -u bench.py --workload $wl $extra > gpurun_out/bench_$wl.json 2> gpurun_out/bench_$wl.err \
         || { echo "BENCH $wl FAILED"; tail -20 gpurun_out/bench_$wl.err; exit 1; }
       cat gpurun_out/bench_$wl.json

@@ -7,8 +7,8 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out/r05_lines
 export TMPDIR=/tmp
 for wl in "$@"; do
-  extra="--cpu-baseline off --ref-gpu off"
-  [ "$wl" = c2 ] && extra=""
+  extra="--full --cpu-baseline off --ref-gpu off"
+  [ "$wl" = c2 ] && extra="--full"
   timeout -k 10 400 python -u bench.py --workload $wl $extra > gpurun_out/r05_lines/bench_$wl.json \
     2> gpurun_out/r05_lines/bench_$wl.err || { echo "BENCH $wl FAILED"; tail -5 gpurun_out/r05_lines/bench_$wl.err; exit 1; }
   python3 - "$wl" <<'PY'
