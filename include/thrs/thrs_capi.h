@@ -28,7 +28,7 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t; /* identical to HIP's own typedef */
 #endif
 
-#define THRS_ABI_VERSION 6
+#define THRS_ABI_VERSION 7
 
 typedef enum thrs_status {
   THRS_SUCCESS = 0,
@@ -161,6 +161,43 @@ int thrs_sort_keys_ex(const thrs_config* config, const thrs_options* options, vo
 int thrs_sort_pairs_ex(const thrs_config* config, const thrs_options* options, void* inputKeyBuffer,
                        void* inputValueBuffer, uint32_t numberOfInputs, void* temporaryBuffer, int startBits,
                        int endBits, hipStream_t stream);
+
+/* Segmented sort (no reference counterpart): many independent ranges of one
+ * buffer sorted by one call.  segOffsets is a DEVICE array of numSegments + 1
+ * non-decreasing u32 values, each <= n; segment s is [segOffsets[s],
+ * segOffsets[s+1]).  Every segment is sorted exactly as thrs_sort_keys /
+ * thrs_sort_pairs would sort it alone (same key image, same window rule,
+ * stable, in place); keys and values outside [segOffsets[0],
+ * segOffsets[numSegments]) are not written.  Asynchronous on the stream: no
+ * host synchronisation, no allocation, and the host never reads segOffsets, so
+ * the sort may be enqueued behind the kernel that produces them.  A segment
+ * whose offsets decrease or end past n is skipped before any of its data is
+ * touched and THRS_ERROR_DEVICE_CHECK is recorded (thrs_check_device_error /
+ * thrs_accumulate_device_error on temporaryBuffer, and the sticky word); the
+ * other segments still sort.  n == 0, numSegments == 0, an empty window or a
+ * window wholly past the key width launch nothing.
+ * Each segment goes to one of three size classes: up to caps[0] keys one wave
+ * sorts it in registers, up to caps[1] one workgroup sorts it in LDS, above
+ * that ONE workgroup streams it through the temporary buffer once per digit:
+ * correct for any size, but a caller with a handful of huge segments should
+ * call thrs_sort_keys / thrs_sort_pairs on each of them instead. */
+/* bytes of the temporary buffer a segmented sort of up to n keys in up to
+ * numSegments segments needs (pairs != 0: with values of config->valueType) */
+int thrs_get_segmented_temporary_bytes(const thrs_config* config, uint32_t n, uint32_t numSegments, int pairs,
+                                       uint64_t* bytes);
+int thrs_sort_segments_keys(const thrs_config* config, void* keys, uint32_t n, const uint32_t* segOffsets,
+                            uint32_t numSegments, void* temporaryBuffer, int startBits, int endBits,
+                            hipStream_t stream);
+int thrs_sort_segments_pairs(const thrs_config* config, void* keys, void* values, uint32_t n,
+                             const uint32_t* segOffsets, uint32_t numSegments, void* temporaryBuffer, int startBits,
+                             int endBits, hipStream_t stream);
+/* class bounds for these types: caps[0] = largest segment the wave class takes,
+ * caps[1] = largest segment the workgroup (in-LDS) class takes.  Host only. */
+int thrs_segment_class_caps(int keyType, int valueBytesOrZero, uint32_t caps[2]);
+/* diagnostic, synchronises: segments of the LAST segmented sort on this buffer
+ * by class: [0] empty or single-key, [1] wave, [2] workgroup, [3] streaming
+ * (rejected segments are in none) */
+int thrs_debug_segment_classes(const void* temporaryBuffer, hipStream_t stream, uint32_t counts[4]);
 
 /* Multi-GPU building block (no reference counterpart -- the reference is
  * single-GPU): ONE stable LSD pass by the 8-bit digit at

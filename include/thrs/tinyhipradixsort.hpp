@@ -175,6 +175,34 @@ class RadixSort {
     checked(temporaryBuffer, stream);
   }
 
+  // extension: segmented sort (thrs_capi.h "Segmented sort").  segOffsets is a
+  // DEVICE array of numSegments + 1 non-decreasing u32 values, each <=
+  // numberOfInputs; every segment is sorted as sortKeys / sortPairs would sort
+  // it alone.  The temporary buffer is sized by
+  // getSegmentedTemporaryBufferBytes, not by getTemporaryBufferBytes.
+  uint64_t getSegmentedTemporaryBufferBytes(uint32_t numberOfMaxInputs, uint32_t numberOfMaxSegments,
+                                            bool pairs) const {
+    const thrs_config c = cconfig();
+    uint64_t bytes = 0;
+    check(thrs_get_segmented_temporary_bytes(&c, numberOfMaxInputs, numberOfMaxSegments, pairs ? 1 : 0, &bytes));
+    return bytes;
+  }
+  void sortKeysSegmented(void* inputKeyBuffer, uint32_t numberOfInputs, const uint32_t* segOffsets,
+                         uint32_t numSegments, void* temporaryBuffer, int startBits, int endBits, oroStream stream) {
+    const thrs_config c = cconfig();
+    check(thrs_sort_segments_keys(&c, inputKeyBuffer, numberOfInputs, segOffsets, numSegments, temporaryBuffer,
+                                  startBits, endBits, reinterpret_cast<hipStream_t>(stream)));
+    checked(temporaryBuffer, stream);
+  }
+  void sortPairsSegmented(void* inputKeyBuffer, void* inputValueBuffer, uint32_t numberOfInputs,
+                          const uint32_t* segOffsets, uint32_t numSegments, void* temporaryBuffer, int startBits,
+                          int endBits, oroStream stream) {
+    const thrs_config c = cconfig();
+    check(thrs_sort_segments_pairs(&c, inputKeyBuffer, inputValueBuffer, numberOfInputs, segOffsets, numSegments,
+                                   temporaryBuffer, startBits, endBits, reinterpret_cast<hipStream_t>(stream)));
+    checked(temporaryBuffer, stream);
+  }
+
   const Config& config() const { return m_config; }
 
   // extension: explicit path / tuning choices (thrs_capi.h thrs_options)

@@ -31,10 +31,11 @@ from dataclasses import dataclass
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libthrs.so")
 TESTUTIL_PATH = os.path.join(_HERE, "libthrs_testutil.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 __all__ = ["KeyType", "ValueType", "SortOrder", "bytesOf", "div_round_up64", "next_multiple64", "Buffer",
-           "RadixSort", "Options", "ThrsError", "lib", "LIB_PATH", "take_device_error"]
+           "RadixSort", "Options", "ThrsError", "lib", "LIB_PATH", "take_device_error", "segment_class_caps",
+           "debug_segment_classes"]
 
 
 class ThrsError(RuntimeError):
@@ -106,6 +107,14 @@ def lib() -> ctypes.CDLL:
         L.thrs_debug_bucket_mode.restype = i32
         L.thrs_debug_vector_tiles.argtypes = [vp, i32, u32, vp, ctypes.POINTER(u32)]
         L.thrs_debug_vector_tiles.restype = i32
+        L.thrs_get_segmented_temporary_bytes.argtypes = [ctypes.POINTER(_CConfig), u32, u32, i32, ctypes.POINTER(u64)]
+        L.thrs_sort_segments_keys.argtypes = [ctypes.POINTER(_CConfig), vp, u32, vp, u32, vp, i32, i32, vp]
+        L.thrs_sort_segments_pairs.argtypes = [ctypes.POINTER(_CConfig), vp, vp, u32, vp, u32, vp, i32, i32, vp]
+        L.thrs_segment_class_caps.argtypes = [i32, i32, ctypes.POINTER(u32)]
+        L.thrs_debug_segment_classes.argtypes = [vp, vp, ctypes.POINTER(u32)]
+        for f in ("thrs_get_segmented_temporary_bytes", "thrs_sort_segments_keys", "thrs_sort_segments_pairs",
+                  "thrs_segment_class_caps", "thrs_debug_segment_classes"):
+            getattr(L, f).restype = i32
         for f in ("thrs_profile_enable", "thrs_profile_read", "thrs_profile_read_kind",
                   "thrs_get_temporary_buffer_bytes", "thrs_sort_keys", "thrs_sort_pairs", "thrs_sort_keys_ex",
                   "thrs_sort_pairs_ex", "thrs_check_device_error", "thrs_accumulate_device_error",
@@ -390,6 +399,36 @@ class RadixSort:
         if checked:
             _check(lib().thrs_check_device_error(_ptr(temporaryBuffer), s))
 
+    def getSegmentedTemporaryBufferBytes(self, numberOfMaxInputs: int, numberOfMaxSegments: int, pairs: bool) -> int:
+        """Bytes of the temporary buffer of sortKeysSegmented / sortPairsSegmented
+        (thrs_get_segmented_temporary_bytes; not getTemporaryBufferBytes)."""
+        out = ctypes.c_uint64()
+        _check(lib().thrs_get_segmented_temporary_bytes(ctypes.byref(self._c()), _n(numberOfMaxInputs),
+                                                        _n(numberOfMaxSegments), int(bool(pairs)), ctypes.byref(out)))
+        return int(out.value)
+
+    def sortKeysSegmented(self, inputKeyBuffer, numberOfInputs: int, segOffsets, numSegments: int, temporaryBuffer,
+                          startBits: int, endBits: int, stream=None, checked: bool = False):
+        """Sorts every segment [segOffsets[s], segOffsets[s+1]) as sortKeys would
+        sort it alone.  segOffsets: device u32[numSegments + 1], never read on
+        the host.  Asynchronous on `stream`; checked as sortKeys."""
+        s = _stream(stream)
+        _check(lib().thrs_sort_segments_keys(ctypes.byref(self._c()), _ptr(inputKeyBuffer), _n(numberOfInputs),
+                                             _ptr(segOffsets), _n(numSegments), _ptr(temporaryBuffer),
+                                             int(startBits), int(endBits), s))
+        if checked:
+            _check(lib().thrs_check_device_error(_ptr(temporaryBuffer), s))
+
+    def sortPairsSegmented(self, inputKeyBuffer, inputValueBuffer, numberOfInputs: int, segOffsets, numSegments: int,
+                           temporaryBuffer, startBits: int, endBits: int, stream=None, checked: bool = False):
+        """As sortKeysSegmented, with values (stable: they follow their keys)."""
+        s = _stream(stream)
+        _check(lib().thrs_sort_segments_pairs(ctypes.byref(self._c()), _ptr(inputKeyBuffer), _ptr(inputValueBuffer),
+                                              _n(numberOfInputs), _ptr(segOffsets), _n(numSegments),
+                                              _ptr(temporaryBuffer), int(startBits), int(endBits), s))
+        if checked:
+            _check(lib().thrs_check_device_error(_ptr(temporaryBuffer), s))
+
     def partitionPass(self, inputKeyBuffer, inputValueBuffer, numberOfInputs: int, temporaryBuffer, outputKeyBuffer,
                       outputValueBuffer, bitLocation: int, counts, stream=None):
         """One stable out-of-place pass by the digit at bitLocation plus its 256
@@ -485,6 +524,23 @@ def debug_big_keys(temporaryBuffer, keyType: int, valueBytes: int, n: int, strea
     _check(lib().thrs_debug_big_keys(_ptr(temporaryBuffer), int(keyType), int(valueBytes), int(n),
                                      _stream(stream), ctypes.byref(out)))
     return int(out.value)
+
+
+def segment_class_caps(keyType, valueBytes: int) -> tuple:
+    """(largest segment of the wave class, largest of the workgroup class) of a
+    segmented sort with these types (thrs_segment_class_caps; host only)."""
+    caps = (ctypes.c_uint32 * 2)()
+    _check(lib().thrs_segment_class_caps(int(keyType), int(valueBytes), caps))
+    return int(caps[0]), int(caps[1])
+
+
+def debug_segment_classes(temporaryBuffer, stream=None) -> tuple:
+    """Segments of the last segmented sort on this buffer by class: (empty or
+    single-key, wave, workgroup, streaming) (thrs_debug_segment_classes;
+    synchronising)."""
+    c = (ctypes.c_uint32 * 4)()
+    _check(lib().thrs_debug_segment_classes(_ptr(temporaryBuffer), _stream(stream), c))
+    return tuple(int(x) for x in c)
 
 
 def debug_vector_tiles(temporaryBuffer, keyType: int, n: int, stream=None) -> int:

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "thrs_host.hpp"
+#include "thrs_segmented.hpp"
 
 namespace thrs_host {
 
@@ -256,6 +257,40 @@ int partition_impl(const thrs_config* cfg, const void* keysIn, const void* valsI
   return THRS_ERROR_INVALID_VALUE;
 }
 
+// thrs_sort_segments_keys / _pairs: host validation in the order of sort_impl
+// (no device call before it is done), then the launch sequence of
+// thrs_segmented.hpp for the key type.
+int segments_impl(const thrs_config* cfg, void* keys, void* vals, bool pairs, uint32_t n, const uint32_t* off,
+                  uint32_t numSegments, void* tmp, int startBits, int endBits, hipStream_t stream) {
+  if (!cfg || !valid_key(cfg->keyType) || (pairs && !valid_value(cfg->valueType))) return THRS_ERROR_INVALID_VALUE;
+  if (cfg->sortOrder != THRS_ORDER_ASCENDING && cfg->sortOrder != THRS_ORDER_DESCENDING) return THRS_ERROR_INVALID_VALUE;
+  if (((endBits - startBits) % 8) != 0) return THRS_ERROR_BIT_RANGE;
+  if (startBits < 0) return THRS_ERROR_INVALID_VALUE;
+  // nothing to do: nothing is launched; the buffer (it holds the header for
+  // any n > 0) reports no device failure afterwards
+  auto noop = [&]() -> int {
+    if (n == 0 || !tmp) return THRS_SUCCESS;
+    return hipMemsetAsync(static_cast<char*>(tmp) + kErrOff, 0, 4, stream) == hipSuccess ? THRS_SUCCESS
+                                                                                         : THRS_ERROR_HIP;
+  };
+  if (n == 0 || numSegments == 0 || startBits >= endBits) return noop();
+  const int width = key_bytes_of(cfg->keyType) * 8;
+  int nPass = 0;  // digits that read at least one key bit; the rest are zero for every key
+  for (int i = 0; startBits + 8 * i < endBits; ++i)
+    if (startBits + 8 * i < width) ++nPass;
+  if (nPass == 0) return noop();
+  if (!keys || !off || !tmp || (pairs && !vals)) return THRS_ERROR_INVALID_VALUE;
+  const int vb = pairs ? value_bytes_of(cfg->valueType) : 0;
+  const bool desc = cfg->sortOrder == THRS_ORDER_DESCENDING;
+  switch (cfg->keyType) {
+    case THRS_KEY_U32: return run_segments<0>(vb, keys, vals, n, off, numSegments, tmp, startBits, nPass, desc, stream);
+    case THRS_KEY_U64: return run_segments<1>(vb, keys, vals, n, off, numSegments, tmp, startBits, nPass, desc, stream);
+    case THRS_KEY_F32: return run_segments<2>(vb, keys, vals, n, off, numSegments, tmp, startBits, nPass, desc, stream);
+    case THRS_KEY_F64: return run_segments<3>(vb, keys, vals, n, off, numSegments, tmp, startBits, nPass, desc, stream);
+  }
+  return THRS_ERROR_INVALID_VALUE;
+}
+
 }  // namespace
 }  // namespace thrs_host
 
@@ -306,6 +341,43 @@ THRS_API int thrs_sort_keys_ex(const thrs_config* config, const thrs_options* op
 THRS_API int thrs_sort_pairs_ex(const thrs_config* config, const thrs_options* options, void* keys, void* values,
                                 uint32_t n, void* tmp, int startBits, int endBits, hipStream_t stream) {
   return sort_impl(config, options, keys, values, true, n, tmp, startBits, endBits, stream);
+}
+
+THRS_API int thrs_get_segmented_temporary_bytes(const thrs_config* cfg, uint32_t n, uint32_t numSegments, int pairs,
+                                                uint64_t* bytes) {
+  if (!cfg || !bytes || !valid_key(cfg->keyType) || (pairs && !valid_value(cfg->valueType)))
+    return THRS_ERROR_INVALID_VALUE;
+  *bytes = seg_layout(key_bytes_of(cfg->keyType), pairs ? value_bytes_of(cfg->valueType) : 0, n, numSegments).bytes;
+  return THRS_SUCCESS;
+}
+
+THRS_API int thrs_sort_segments_keys(const thrs_config* config, void* keys, uint32_t n, const uint32_t* segOffsets,
+                                     uint32_t numSegments, void* tmp, int startBits, int endBits, hipStream_t stream) {
+  return segments_impl(config, keys, nullptr, false, n, segOffsets, numSegments, tmp, startBits, endBits, stream);
+}
+
+THRS_API int thrs_sort_segments_pairs(const thrs_config* config, void* keys, void* values, uint32_t n,
+                                      const uint32_t* segOffsets, uint32_t numSegments, void* tmp, int startBits,
+                                      int endBits, hipStream_t stream) {
+  return segments_impl(config, keys, values, true, n, segOffsets, numSegments, tmp, startBits, endBits, stream);
+}
+
+THRS_API int thrs_segment_class_caps(int keyType, int valueBytesOrZero, uint32_t caps[2]) {
+  if (!caps || !valid_key(keyType) ||
+      !(valueBytesOrZero == 0 || valueBytesOrZero == 4 || valueBytesOrZero == 8 || valueBytesOrZero == 16))
+    return THRS_ERROR_INVALID_VALUE;
+  caps[0] = seg_cap_wave();
+  caps[1] = seg_cap_block(key_bytes_of(keyType));
+  return THRS_SUCCESS;
+}
+
+THRS_API int thrs_debug_segment_classes(const void* tmp, hipStream_t stream, uint32_t counts[4]) {
+  if (!tmp || !counts) return THRS_ERROR_INVALID_VALUE;
+  if (hipMemcpyAsync(counts, static_cast<const char*>(tmp) + kCounterOff, 16, hipMemcpyDeviceToHost, stream) !=
+          hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return THRS_ERROR_HIP;
+  return THRS_SUCCESS;
 }
 
 THRS_API int thrs_partition_pass(const thrs_config* config, const void* keysIn, const void* valuesIn, uint32_t n,
